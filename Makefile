@@ -1,7 +1,7 @@
 # lws-amd developer targets (reference Makefile analogue)
 PY ?= python3
 
-.PHONY: build test test-integration test-e2e test-gpu bench bench-ds smoke lint plan-steps manager clean
+.PHONY: build test test-integration test-e2e test-gpu bench bench-full bench-ds smoke lint plan-steps manager clean
 
 build:          ## build the gfx950 HIP kernel extension in-tree
 	$(PY) -m lws_amd.ops.build
@@ -25,6 +25,9 @@ test-gpu:       ## MI355X tier (kernel numerics vs fp32 reference, HIP engine)
 
 bench:          ## flagship benchmark (BASELINE.json metric), 1 GPU
 	$(PY) bench.py --gpus 1 --steps 3 --warmup 1
+
+bench-full:     ## headline + supplementary decode throughput (bf16, fp8)
+	$(PY) bench.py --gpus 1 --steps 3 --warmup 1 --full
 
 bench-ds:       ## DisaggregatedSet lifecycle benchmark (config #4)
 	$(PY) scripts/bench_ds.py --model llama-3-8b --steps 3 --warmup 1

@@ -18,6 +18,14 @@ Launch (the driver does this):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run measures only the headline: set up, warm up, time the K
+lifecycles, print the result line.  `--full` adds the supplementary
+serving decode throughput (bf16, and fp8 at TP=1 on GPU) after the timed
+steps.  `--dump-outputs DIR` writes what the last timed lifecycle
+computed (rank 0's Ready shard: the warmup's KV-cache page of every layer
+and a fixed weight sample) as float32 DIR/<name>.npy; the inputs are fully
+determined by the arguments, so two builds can be compared array by array.
+
 Rank 0 hosts the control plane + shard 0; other ranks host shards and
 follow broadcast commands (lws_amd/serving/runtime.py).  Rank 0 prints one
 JSON line.  scaling="strong": the model is fixed; more GPUs mean smaller
@@ -70,8 +78,72 @@ def parse_args():
     p.add_argument("--prompt-len", type=int, default=128)
     p.add_argument("--decode-steps", type=int, default=32)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--skip-decode-bench", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the supplementary measurements (serving "
+                        "decode throughput, bf16 and fp8) after the timed "
+                        "steps; a plain run only measures the headline")
+    p.add_argument("--skip-decode-bench", action="store_true",
+                   help="with --full: leave the decode measurements out")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (rank 0's "
+                        "shard) as DIR/<name>.npy")
     return p.parse_args()
+
+
+# first page BlockAllocator hands out: the readiness warmup's sequence
+# (4 prompt tokens + 1 decoded) lives there, page 0 is the scratch page
+WARMUP_PAGE = 1
+WEIGHT_SAMPLE_ROWS = 8
+WEIGHT_SAMPLE_COLS = 128
+
+
+def capture_outputs(engine) -> dict:
+    """Device-side snapshot of what group bring-up left in a Ready engine.
+
+    The lifecycle's numerical product is the engine shard itself: seeded
+    weights plus the KV pool the warmup prefill + decode wrote through
+    every layer (layer l's K/V rows depend on all kernels of layers < l:
+    norms, projections, rope, prefill/paged attention, MLP; the decoded
+    position additionally on the logits argmax).  Only small slices are
+    cloned here, inside the lifecycle; conversion to numpy happens after
+    the timed block.
+    """
+    k = torch.stack([kc[WARMUP_PAGE] for kc, _ in engine.kv_caches])
+    v = torch.stack([vc[WARMUP_PAGE] for _, vc in engine.kv_caches])
+    r, c = WEIGHT_SAMPLE_ROWS, WEIGHT_SAMPLE_COLS
+    w = torch.stack([layer.qkv.weight[:r, :c]
+                     for layer in engine.model.layers])
+    out = {"warmup_k_cache": k, "warmup_v_cache": v, "qkv_weight_sample": w}
+    if engine.model.lm_head is not None:
+        out["lm_head_weight_sample"] = engine.model.lm_head.weight[:r, :c] \
+            .clone()
+    return out
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(outputs: dict, directory: str,
+                 budget_bytes: int = DUMP_BUDGET_BYTES) -> None:
+    """Write each array as float32 DIR/<name>.npy, at most budget_bytes in
+    all.  Llama-3-70B needs ~10 MiB (2 x 80 layers x 8 kv heads x 16 slots
+    x 128 x 4 B); an array over its equal share of the budget is replaced
+    by a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = budget_bytes // (4 * max(1, len(outputs)))     # elements each
+    total = 0
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(t.numel(), (share,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.to(torch.float32).cpu().numpy()
+        total += arr.nbytes
+        np.save(os.path.join(directory, f"{name}.npy"), arr)
+    assert total <= budget_bytes, (total, budget_bytes)
 
 
 def build_lws(args, size: int):
@@ -170,7 +242,7 @@ class BenchConductor:
             assert env["NODE_RANK"] == widx
         self.env_checked = True
 
-    def run_cycle(self, seed_extra: int) -> dict:
+    def run_cycle(self, seed_extra: int, capture: bool = False) -> dict:
         args = self.args
         store = self.cluster.store
         t0 = time.perf_counter()
@@ -215,6 +287,11 @@ class BenchConductor:
                   f"live={[(p.metadata.name, p.metadata.uid) for p in live]}",
                   file=sys.stderr, flush=True)
 
+        # the Ready engine of the rolled-out revision is the lifecycle's
+        # product; snapshot it before teardown frees it
+        outputs = (capture_outputs(self.conductor.host.engine)
+                   if capture else None)
+
         # teardown
         store.delete(lwsapi.KIND, "default", "bench-lws",
                      propagation="Background")
@@ -238,7 +315,7 @@ class BenchConductor:
             raise
         self.conductor.command({"op": "teardown"})
         return {"time_to_ready_s": t_ready, "rollout_s": t_rollout,
-                "shard": shard_info}
+                "shard": shard_info, "outputs": outputs}
 
     def decode_bench(self, weight_dtype: str = "bf16") -> dict:
         args = self.args
@@ -320,13 +397,19 @@ def main() -> None:
             bc.run_cycle(seed_extra=1000 + w)
 
         bc.conductor.command({"op": "block_begin"})
-        results = [bc.run_cycle(seed_extra=i) for i in range(args.steps)]
+        results = [bc.run_cycle(seed_extra=i,
+                                capture=(args.dump_outputs is not None
+                                         and i == args.steps - 1))
+                   for i in range(args.steps)]
         acks = bc.conductor.command({"op": "block_end"})
         elapsed = max(a for a in acks if isinstance(a, float))
 
+        if args.dump_outputs is not None and results:
+            dump_outputs(results[-1]["outputs"], args.dump_outputs)
+
         decode = None
         decode_fp8 = None
-        if not args.skip_decode_bench:
+        if args.full and not args.skip_decode_bench:
             decode = bc.decode_bench()
             if is_gpu and world == 1:
                 # supplementary: the fp8 serving mode's decode throughput
@@ -397,9 +480,14 @@ def main() -> None:
         _teardown_dist()
         sys.stdout.flush()
         sys.stderr.flush()
-        # hard exit: the control-plane daemon threads and the gloo
-        # destructor must not block process death
-        os._exit(0 if ok else 1)
+        if world > 1:
+            # hard exit: the gloo destructor must not block process death
+            os._exit(0 if ok else 1)
+    # single process: the control-plane threads are all daemons and there
+    # is no process group, so leave through the normal interpreter exit:
+    # exit handlers and library finalizers (a profiler flushing its trace
+    # of this run, for one) only fire on this path
+    sys.exit(0 if ok else 1)
 
 
 if __name__ == "__main__":

@@ -30,16 +30,74 @@ def _parse_json_line(stdout):
 
 
 def test_bench_single_process():
-    r = _run_bench({}, ["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    r = _run_bench({}, ["--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--full"])
     assert r.returncode == 0, r.stderr[-4000:]
     out = _parse_json_line(r.stdout)
     assert out["n_gpus"] == 1
     assert out["steps"] == 2
+    assert out["ms_per_step"] > 0
     assert out["higher_is_better"] is False
     assert out["value"] > 0
     assert out["config"]["rollout_ms_p50"] > 0
     assert out["config"]["decode_tokens_per_s"] > 0
     assert out["config"]["parallelism"] == "tp1"
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain run measures the headline only (no decode figures), and
+    --dump-outputs writes float32 arrays that are identical from run to
+    run with the same arguments."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = _run_bench({}, ["--gpus", "1", "--steps", "2", "--warmup", "0",
+                            "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-4000:]
+        out = _parse_json_line(r.stdout)
+        assert out["steps"] == 2
+        assert out["ms_per_step"] > 0
+        assert out["config"]["decode_tokens_per_s"] is None
+        dumps.append({p.name: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == set(b) == {"warmup_k_cache.npy", "warmup_v_cache.npy",
+                                "qkv_weight_sample.npy",
+                                "lm_head_weight_sample.npy"}
+    for name, arr in a.items():
+        assert arr.dtype == np.float32
+        assert np.isfinite(arr).all()
+        assert np.array_equal(arr, b[name]), name
+    # the warmup wrote 5 positions (4 prompt + 1 decoded) of the page in
+    # every layer; the rest of the page is still the zero-initialised pool
+    k = a["warmup_k_cache.npy"]                # [L, Hkv, page, D]
+    assert (np.abs(k[:, :, :5]).max(axis=(0, 1, 3)) > 0).all()
+    assert not k[:, :, 5:].any()
+    assert sum(arr.nbytes for arr in a.values()) <= 64 * 2 ** 20
+
+
+def test_dump_outputs_holds_its_size_budget(tmp_path):
+    """An array over its share of the byte budget is replaced by a fixed
+    seeded sample, so the limit holds for any model size."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    assert bench.DUMP_BUDGET_BYTES == 64 * 2 ** 20
+    outs = {"big": torch.arange(1000, dtype=torch.bfloat16),
+            "small": torch.ones(10)}
+    for name in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / name), budget_bytes=400)
+    big = np.load(tmp_path / "a" / "big.npy")
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert big.dtype == small.dtype == np.float32
+    assert big.shape == (50,) and small.shape == (10,)
+    assert big.nbytes + small.nbytes <= 400
+    assert np.isin(big, outs["big"].float().numpy()).all()
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
 
 
 def _two_rank_attempt(port, timeout=240):
@@ -54,7 +112,7 @@ def _two_rank_attempt(port, timeout=240):
                "--device", "cpu", "--model", "llama-tiny", "--kv-pages", "64",
                "--decode-batch", "4", "--prompt-len", "16",
                "--decode-steps", "4", "--gpus", "2", "--steps", "1",
-               "--warmup", "0"]
+               "--warmup", "0", "--full"]
         procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True,
                                       env=p_env, cwd=REPO))
@@ -101,7 +159,8 @@ def test_bench_four_rank_gloo():
                    "--device", "cpu", "--model", "llama-tiny4",
                    "--kv-pages", "64", "--decode-batch", "4",
                    "--prompt-len", "16", "--decode-steps", "2",
-                   "--gpus", "4", "--steps", "1", "--warmup", "0"]
+                   "--gpus", "4", "--steps", "1", "--warmup", "0",
+                   "--full"]
             procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE,
                                           stderr=subprocess.PIPE, text=True,
                                           env=p_env, cwd=REPO))

@@ -156,7 +156,7 @@ def test_bench_two_rank_gpu():
                "--model", "llama-tiny", "--kv-pages", "64",
                "--decode-batch", "4", "--prompt-len", "16",
                "--decode-steps", "4", "--gpus", "2", "--steps", "1",
-               "--warmup", "0"]
+               "--warmup", "0", "--full"]
         procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True,
                                       env=env, cwd=REPO))
